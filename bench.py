@@ -9,7 +9,18 @@ all_gather (RCCL over xGMI) replicates them; every rank then holds a replica of
 the ring and routes its own slice of the global key stream (keys[q] =
 splitmix(seed, q), src[q] = q mod N): weak scaling, no collective in the timed
 data path, the barrier and the max-over-ranks timing are the only cross-rank
-traffic.  After the timed region the same run measures, on every rank:
+traffic.  A plain run sets up, warms up, times the K steps, writes its outputs
+if --dump-outputs DIR is given and prints the result line (metric, value,
+ms_per_step, kernel_ms, the setup times); everything below takes runs of its
+own and is measured with --full only.  --dump-outputs DIR writes what the last
+timed step returned to its caller on rank 0 -- owner, hops, status, one value
+per lookup -- as DIR/<name>.npy (float32; a fixed, seeded sample of the batch
+when the whole of it would exceed DUMP_BUDGET bytes).
+
+With --full the run also measures, before the timed region, the ring sort
+(both variants) and a second finger build into the mapped tables, and after it
+the headline's checks and roofline (counting build, exact successors, gather
+probe, random sources, small batches), then on every rank:
 
   arc      C4 as BASELINE.json states it -- the ring sharded by key arc, each
            rank holding route rows for its arc only, lookups exchanged with
@@ -28,7 +39,7 @@ traffic.  After the timed region the same run measures, on every rank:
            is closed: one cx_dhash_maintenance pass per step, keys sharded
            over ranks (strong scaling), parity against the oracle on a sample.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 With --gpus N > 1 and no torch.distributed environment, bench.py starts
@@ -261,6 +272,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--peers-log2", type=int, default=24)
     ap.add_argument("--keys-log2", type=int, default=25, help="keys per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the checks, rooflines, CPU baselines and the sub-record legs "
+                         "(arc, churn, cpu, c5, c2, c3); the --no-* and leg options below apply "
+                         "to such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's owner, hops and status "
+                         "(rank 0) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
                     help="target wall time of the CPU-oracle baseline sample")
     ap.add_argument("--no-cpu", action="store_true")
@@ -380,7 +398,8 @@ def dry_run(args):
     """CX_BENCH_DRYRUN=1: the launch / rendezvous / timing / reduction /
     reporting flow without a GPU (CPU tests of the N > 1 path over gloo): a
     2^12-peer ring, the whole-node roofline reduction fed with zero bytes, and
-    the CPU baseline on rank 0 at every world size, as in the GPU run."""
+    with --full the CPU baseline on rank 0 at every world size, as in the GPU
+    run."""
     world, rank, _ = dist.env_rank()
     dist.init("gloo")
     dist.barrier(world)
@@ -389,7 +408,7 @@ def dry_run(args):
     dt_max = dist.max_over_ranks(time.perf_counter() - t0, world)
     roof = whole_node_roofline(0, 1.0, world, None)
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         import oracle as O
         ring_np = O.ring_build(O.splitmix_keys(SEED_RING, 1 << 12))
         F = O.fingers(ring_np, threads=2)
@@ -421,7 +440,7 @@ def setup_ring(args, world, rank, dev, backend):
     ring = chordx.Ring(ids, device=dev.index or 0)
     torch.cuda.synchronize(dev)
     t_ring = time.perf_counter() - t0
-    setup_ring.sort_roofline = sort_roofline(ids)
+    setup_ring.sort_roofline = sort_roofline(ids) if args.full else None
     return ring, t_gather, t_ring
 
 
@@ -458,6 +477,34 @@ def sort_roofline(ids):
                    "the default is MSD with the LSD sort (4 tag + 16 key passes) as the "
                    "fallback for a bucket above 2048 keys")
     return out
+
+
+DUMP_BUDGET = 48 << 20       # bytes of .npy payload per --dump-outputs run
+SEED_DUMP_SAMPLE = 0x5EED00D0  # the sample of lookups dumped when the batch is larger
+
+
+def dump_outputs(path, rank, n_peers, owner, hops, status):
+    """--dump-outputs: rank 0 writes the arrays the timed path handed back in
+    its last step -- owner (ring index), hops, status per lookup -- as
+    <path>/<name>.npy.  float32 holds each value exactly (owner as float64 on
+    a ring above 2^24 peers).  A batch whose arrays exceed DUMP_BUDGET is
+    sampled: the same sorted lookup indices for all three arrays, drawn
+    without replacement by a seeded generator, so two builds run with the same
+    arguments write the same lookups."""
+    if rank != 0:
+        return
+    os.makedirs(path, exist_ok=True)
+    q = owner.shape[0]
+    owner_t = np.float32 if n_peers <= 1 << 24 else np.float64
+    m = min(q, DUMP_BUDGET // (np.dtype(owner_t).itemsize + 8))
+    idx = None
+    if m < q:
+        idx = np.sort(np.random.default_rng(SEED_DUMP_SAMPLE).choice(q, size=m, replace=False))
+        idx = torch.from_numpy(idx).to(owner.device)
+    for name, t, dt in (("owner", owner, owner_t), ("hops", hops, np.float32),
+                        ("status", status, np.float32)):
+        a = (t if idx is None else t[idx]).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a.astype(dt))
 
 
 def time_steps(fn, steps, world, dev):
@@ -1214,6 +1261,17 @@ def c3_leg(args, world, rank, dev):
             "oracle_sample_keys": m, "cpu_baseline": cpu}
 
 
+def c4_config(args, world, N, Q):
+    """The `config` record of the replicated C4 headline."""
+    return {
+        "workload": "C4 finger-routed lookups with hop counts (per GPU): "
+                    f"2^{args.peers_log2}-peer ring, 2^{args.keys_log2} keys/GPU/step, "
+                    "src = q mod N, splitmix seeds 0x5EED0005/0x5EED0006",
+        "peers": N, "keys_per_gpu": Q, "global_batch": world * Q,
+        "parallelism": f"ring IDs all-gathered, replicated route tables, keys sharded "
+                       f"x{world} (arc-sharded all_to_all-v layout: `arc`)"}
+
+
 def headline_line(args, world, N, Q, dt_max, roof, traffic, kernel_name, algo_bytes, kern_ms,
                   ref_bytes, gather, route_variant, table_bytes, cz_escapes, sum_hops, hist,
                   max_hops, bad, owner_eq, counting_same, succ_ms, small, rsrc_ms, rsrc_bad,
@@ -1222,13 +1280,7 @@ def headline_line(args, world, N, Q, dt_max, roof, traffic, kernel_name, algo_by
     legs (churn_route_ready, arc, cpu_baseline, c5, c2, c3) fill their keys
     as they finish (LegGuard prints the line as it stands if one hangs)."""
     total = world * Q * args.steps
-    line = line_base(args, world, total / dt_max, dt_max, {
-        "workload": "C4 finger-routed lookups with hop counts (per GPU): "
-                    f"2^{args.peers_log2}-peer ring, 2^{args.keys_log2} keys/GPU/step, "
-                    "src = q mod N, splitmix seeds 0x5EED0005/0x5EED0006",
-        "peers": N, "keys_per_gpu": Q, "global_batch": world * Q,
-        "parallelism": f"ring IDs all-gathered, replicated route tables, keys sharded "
-                       f"x{world} (arc-sharded all_to_all-v layout: `arc`)"})
+    line = line_base(args, world, total / dt_max, dt_max, c4_config(args, world, N, Q))
     roof.update({
         "traffic": None if traffic is None else traffic * world,
         "traffic_note": "PMC FETCH_SIZE + WRITE_SIZE per launch on one GPU "
@@ -1314,6 +1366,8 @@ def main_arc(args):
     router.records_sent = 0
     _, dt_max = time_steps(lambda: router.route(src, keys, owner, hops, status), args.steps,
                            world, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, ring.n, owner, hops, status)
     bad = dist.sum_over_ranks(int((status != 0).sum().item()), world, dev)
     sent = dist.sum_over_ranks(router.records_sent, world, dev)
     sum_hops = dist.sum_over_ranks(int(hops.to(torch.int64).sum().item()), world, dev)
@@ -1370,15 +1424,17 @@ def main():
     ring.sync()
     t_fing = time.perf_counter() - t0
     st1 = chordx.pool_stats()
-    t0 = time.perf_counter()
-    ring.build_fingers()  # same tables again: their HBM is now mapped
-    ring.sync()
-    t_fing_warm = time.perf_counter() - t0
-    setup_alloc = {k: {"fresh_GiB": d["fresh_bytes"] / 2**30, "pooled_GiB": d["reused_bytes"] / 2**30,
-                       "retries": d["retries"]}
-                   for k, d in (("fingers_build", chordx.pool_stats_delta(st0, st1)),
-                                ("fingers_build_again",
-                                 chordx.pool_stats_delta(st1, chordx.pool_stats())))}
+    t_fing_warm = setup_alloc = None
+    if args.full:
+        t0 = time.perf_counter()
+        ring.build_fingers()  # same tables again: their HBM is now mapped
+        ring.sync()
+        t_fing_warm = time.perf_counter() - t0
+        setup_alloc = {k: {"fresh_GiB": d["fresh_bytes"] / 2**30,
+                           "pooled_GiB": d["reused_bytes"] / 2**30, "retries": d["retries"]}
+                       for k, d in (("fingers_build", chordx.pool_stats_delta(st0, st1)),
+                                    ("fingers_build_again",
+                                     chordx.pool_stats_delta(st1, chordx.pool_stats())))}
     keys = torch.empty((Q, 2), dtype=torch.int64, device=dev)
     q0, q1 = dist.shard(rank, Q)
     chordx.fill_splitmix(keys, SEED_KEYS, offset=q0)
@@ -1412,7 +1468,30 @@ def main():
     dist.barrier(world)
     dt = time.perf_counter() - t0
     dt_max = dist.max_over_ranks(dt, world, dev)
-    kern_ms = ev0.elapsed_time(ev1) / args.steps  # one cx_route launch per step
+    kern_ms = ev0.elapsed_time(ev1) / max(1, args.steps)  # one cx_route launch per step
+    if args.dump_outputs:
+        progress("writing outputs")
+        dump_outputs(args.dump_outputs, rank, ring.n, owner, hops, status)
+
+    if not args.full:
+        # ---- a plain run: the headline alone ----
+        kern_ms_max = dist.max_over_ranks(kern_ms, world, dev)
+        if rank == 0:
+            line = line_base(args, world, world * Q * args.steps / dt_max, dt_max,
+                             c4_config(args, world, N, Q))
+            line.update({
+                "kernel": kernel_name, "kernel_ms": kern_ms_max,
+                "route_variant": route_variant, "route_table_bytes": table_bytes,
+                "setup_s": {"id_all_gather": t_gather, "ring_sort": t_ring,
+                            "fingers_build": t_fing},
+                "full": False,
+                "note": "checks, rooflines, CPU baselines and the arc / churn / c5 / c2 / c3 "
+                        "sub-records: --full"})
+            print(json.dumps(line), flush=True)
+        ring.close()
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
 
     # ---- results (all reduced over ranks) ----
     progress("timed steps done; checks")

@@ -424,7 +424,7 @@ def test_bench_launches_n_ranks_itself():
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(CX_BENCH_DRYRUN="1", CX_DIST_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full",
                         "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"], env=env,
                        capture_output=True,
                        text=True, timeout=300)
